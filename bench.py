@@ -14,8 +14,12 @@ slab of the M-GPU layout on one GPU (per-rank rehearsal of the multi-GPU shapes)
 
 value = dst voxels of all ranks / wall time per step (Gvoxels/s).  roofline: the dominant
 kernel (SumRange: 6 B/voxel algorithmic) timed with HIP events on the library's compute
-stream.  After the timed region, secondary measurements go into the same JSON line (none of
-them is `value`):
+stream, inside the timed steps.  A plain run does that and no more: it sets up, warms up, times
+--steps steps, writes the last step's R and D with --dump-outputs DIR (DIR/resample_dst.npy and
+DIR/sumrange_dst.npy: the UInt16 codes as float32, a fixed seeded sample of volumes above 2^22
+voxels; the inputs are seeded, so every run with the same arguments writes the same files) and
+prints the line.  With --full, secondary measurements follow the timed region and go into the
+same JSON line (none of them is `value`):
   * mapping_m1_3   -- the same pipeline with mapping [-1, 3] on every volume (the float-codec
                       kernels; SURVEY §8(d) "a second run uses mapping [-1,3]");
   * f32_linear     -- Float32 "Linear" Resample with the z+1 halo plane exchanged between
@@ -59,6 +63,13 @@ def parse():
     # default warm-up covers ~35 ms; an explicit --warmup is honoured as given
     p.add_argument("--warmup", type=int, default=25)
     p.add_argument("--dst", type=int, default=1024, help="per-GPU dst cube edge (source = dst/2)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also take the secondary measurements (mapping [-1,3], "
+                        "Float32 Linear, config 4, migrate, copy peak, CPU baseline); the --no-* options "
+                        "drop single ones of them")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed to DIR/<name>.npy "
+                        "(float32 codes; a fixed seeded sample of volumes above the size limit)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-copy-peak", action="store_true", help="skip the library-Copy achievable peak")
     p.add_argument("--no-secondary", action="store_true",
@@ -82,7 +93,45 @@ def parse():
     p.add_argument("--secondary-timeout", type=float, default=120.0,
                    help="seconds one secondary measurement may take before the watchdog prints the line "
                         "with that field {'error': 'timeout'} and exits non-zero")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:
+        # a plain run is the headline alone: set up, warm up, time the steps, print the line
+        args.no_secondary = args.no_config4 = args.no_migrate = args.no_copy_peak = args.no_cpu_baseline = True
+    return args
+
+
+DUMP_SAMPLE = 1 << 22   # voxels written per volume by --dump-outputs (16 MiB of float32 each)
+
+
+def dump_sample_index(n):
+    """Flat voxel indices --dump-outputs writes of an n-voxel volume: None (all of it) up to
+    DUMP_SAMPLE voxels, else DUMP_SAMPLE sorted indices drawn with a fixed seed -- the same ones
+    in every run and for every volume of that size."""
+    import numpy as np
+
+    if n <= DUMP_SAMPLE:
+        return None
+    return np.sort(np.random.default_rng(0x5EED).integers(0, n, DUMP_SAMPLE))
+
+
+def dump_outputs(torch, slab, directory, volumes, rank):
+    """--dump-outputs: the UInt16 codes of each (name, view) as float32 in directory/<name>.npy
+    (<name>.rank<r>.npy for r > 0): the whole volume shaped (z, y, x), or the voxels at
+    dump_sample_index() of a larger one, so two builds are compared voxel for voxel."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, v in volumes:
+        n = v.dimX * v.dimY * v.dimZ
+        codes = slab.device_tensor(v.data, 2 * n).view(torch.int16)
+        idx = dump_sample_index(n)
+        if idx is not None:
+            codes = codes[torch.from_numpy(idx).cuda()]
+        else:
+            codes = codes.view(v.dimZ, v.dimY, v.dimX)
+        arr = codes.cpu().numpy().view(np.uint16).astype(np.float32)
+        np.save(os.path.join(directory, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
 
 
 def global_dims(edge, n):
@@ -247,6 +296,10 @@ def main():
 
     elapsed, (res_ms, sum_ms) = ctx.timed(pipeline((sview, rview, bview, dview)), args.steps, args.warmup, 2)
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs:
+        # what a caller of the two timed calls holds after the last step: R (Resample's dst) and
+        # D (SumRange's dst); written before any secondary measurement reuses the buffers
+        dump_outputs(torch, slab, args.dump_outputs, (("resample_dst", rview), ("sumrange_dst", dview)), rank)
     vox_rank = DX * DY * (dz1 - dz0)
     total_vox = vox_rank * world
     value = total_vox / (ms_per_step / 1e3) / 1e9

@@ -15,5 +15,5 @@ step() {  # name, limit, command...
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
 step pytest_gpu 900 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread || exit 1
-step bench 300 python bench.py || exit 1
+step bench 300 python bench.py --full || exit 1
 echo done

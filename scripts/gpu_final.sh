@@ -22,10 +22,10 @@ step() {  # name, limit, command...
     return $rc
 }
 if [ "$PART" = 1 ]; then
-    B="python3 bench.py --no-cpu-baseline --no-copy-peak --no-config4"
+    B="python3 bench.py --full --no-cpu-baseline --no-copy-peak --no-config4"
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
     step pytest_gpu 900 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread || exit 1
-    step bench 300 python bench.py || exit 1
+    step bench 300 python bench.py --full || exit 1
     step prof_trace 300 rocprofv3 --kernel-trace --stats -d $O/prof/trace -o run --output-format csv -- $B || exit 1
     step prof_fetch 300 rocprofv3 --pmc FETCH_SIZE -d $O/prof/fetch -o run --output-format csv -- $B || exit 1
     step prof_write 300 rocprofv3 --pmc WRITE_SIZE -d $O/prof/write -o run --output-format csv -- $B || exit 1

@@ -34,12 +34,61 @@ def test_config4_strong_layout(n):
     assert planes == list(range(2048))
 
 
+def test_dump_sample_is_fixed_and_within_the_size_limit():
+    assert bench.dump_sample_index(bench.DUMP_SAMPLE) is None          # written whole
+    n = 1024 ** 3
+    idx = bench.dump_sample_index(n)
+    assert idx.shape == (bench.DUMP_SAMPLE,) and idx[0] >= 0 and idx[-1] < n
+    assert (idx[1:] >= idx[:-1]).all()
+    assert (bench.dump_sample_index(n) == idx).all()                   # the same voxels in every run
+    assert 2 * bench.DUMP_SAMPLE * 4 <= 64e6                           # R and D as float32
+
+
+SECONDARY = ("mapping_m1_3", "f32_linear", "f32_linear_native", "config4_2048", "migrate", "copy_peak",
+             "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A run without --full prints the headline fields and none of the secondary measurements;
+    --dump-outputs writes R and D of the last timed step, here (256^3 dst > DUMP_SAMPLE voxels)
+    the seeded sample, equal to the oracle's pipeline on the same synthetic inputs."""
+    import numpy as np
+    from oracle import binding as ob
+
+    e = 256
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dst", str(e), "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup",
+                "config", "roofline"):
+        assert key in out, key
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert not [k for k in SECONDARY if k in out] and "frac_vs_copy_peak" not in out["roofline"]
+
+    src = ob.Volume(ob.synth_codes((e // 2,) * 3, 5, 0x5EED), 5)
+    b = ob.Volume(ob.synth_codes((e,) * 3, 5, 0x5EED + 1), 5)
+    rr, d = ob.Volume.zeros((e,) * 3, 5), ob.Volume.zeros((e,) * 3, 5)
+    ob.resample(rr, src, 1)
+    ob.arith_range("Sum", d, rr, b, (0, 0, 0), (e,) * 3)
+    idx = bench.dump_sample_index(e ** 3)
+    assert sorted(os.listdir(tmp_path / "out")) == ["resample_dst.npy", "sumrange_dst.npy"]
+    for name, ref in (("resample_dst", rr), ("sumrange_dst", d)):
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == idx.shape
+        np.testing.assert_array_equal(got, ref.codes.reshape(-1)[idx].astype(np.float32), err_msg=name)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", [0, 2, 4])
 def test_bench_config4_layout_rehearsal(layout):
     """config4_2048 on one GPU: the whole fixed volume (layout 0) or rank 0's slab of the
     2- / 4-GPU layout, at a reduced edge."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dst", "128", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dst", "128", "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline", "--no-copy-peak", "--no-secondary", "--config4-edge", "512"]
     if layout:
         cmd += ["--layout-gpus", str(layout)]
@@ -55,7 +104,7 @@ def test_bench_config4_layout_rehearsal(layout):
 
 @pytest.mark.gpu
 def test_bench_small_run_prints_one_contract_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dst", "128", "--steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dst", "128", "--steps", "3",
                         "--warmup", "2", "--cpu-dst", "64", "--config4-edge", "256"], capture_output=True, text=True,
                        timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -92,7 +141,7 @@ def test_bench_native_comm_leg_on_one_rank():
     and vktHipResampleSlabOverlapped) end to end on a one-rank communicator; its dst bytes equal
     the torch-transport leg's.  At N>1 with the nccl backend the same leg moves the halo over
     RCCL between GPUs (the driver's 8-GPU run)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dst", "128", "--steps", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dst", "128", "--steps", "4",
                         "--warmup", "1", "--no-cpu-baseline", "--no-copy-peak", "--no-config4", "--no-migrate",
                         "--native-comm"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -142,7 +142,7 @@ def test_config4_rank_slab_full_size(hip, rank):
 
 def test_bench_layout8_rank0_runs():
     """bench.py --layout-gpus 8: rank 0's config-4 slab (2048x2048x256 dst) in the bench harness."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layout-gpus", "8", "--steps", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--layout-gpus", "8", "--steps", "5",
                           "--warmup", "2", "--no-cpu-baseline", "--no-copy-peak"], capture_output=True, text=True,
                          timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
