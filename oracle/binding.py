@@ -38,6 +38,8 @@ class _Vol(C.Structure):
 
 _lib.vko_map.argtypes = [C.POINTER(C.c_uint8), C.c_float, C.c_int32, C.c_float, C.c_float]
 _lib.vko_unmap.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_int32, C.c_float, C.c_float]
+_lib.vko_map_n.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.c_float, C.c_float]
+_lib.vko_unmap_n.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.c_float, C.c_float]
 _lib.vko_fill_range.argtypes = [C.POINTER(_Vol), _i3, _i3, C.c_float]
 _lib.vko_copy_range.argtypes = [C.POINTER(_Vol), C.POINTER(_Vol), _i3, _i3, _i3]
 _lib.vko_arith_range.argtypes = [C.c_int32, C.POINTER(_Vol), C.POINTER(_Vol), C.POINTER(_Vol), _i3, _i3, _i3]
@@ -106,6 +108,22 @@ def unmap_voxel(data: bytes, fmt: int, lo: float = 0.0, hi: float = 1.0) -> floa
     v = C.c_float(0.0)
     _lib.vko_unmap(C.byref(v), buf, fmt, lo, hi)
     return v.value
+
+
+def map_array(values, fmt: int, lo: float = 0.0, hi: float = 1.0, init=0) -> np.ndarray:
+    """MapVoxel over a float32 array -> codes (formats the codec does not write keep `init`)."""
+    vals = np.ascontiguousarray(values, dtype=np.float32)
+    codes = np.full(vals.shape, init, dtype=CODE_DTYPE[fmt])
+    _lib.vko_map_n(codes.ctypes.data, vals.ctypes.data, vals.size, BPV[fmt], fmt, lo, hi)
+    return codes
+
+
+def unmap_array(codes, fmt: int, lo: float = 0.0, hi: float = 1.0, init=0.0) -> np.ndarray:
+    """UnmapVoxel over a code array -> float32 (formats the codec does not read keep `init`)."""
+    c = np.ascontiguousarray(codes, dtype=CODE_DTYPE[fmt])
+    vals = np.full(c.shape, init, dtype=np.float32)
+    _lib.vko_unmap_n(vals.ctypes.data, c.ctypes.data, c.size, BPV[fmt], fmt, lo, hi)
+    return vals
 
 
 def fill_range(v: Volume, first, last, value: float) -> None:

@@ -129,6 +129,19 @@ void vko_unmap(float* value, const uint8_t* src, int32_t fmt, float lo, float hi
     }
 }
 
+/* n voxels at a stride of `bpv` bytes (test drivers: whole code spaces in one call) */
+void vko_map_n(uint8_t* dst, const float* values, size_t n, size_t bpv, int32_t fmt, float lo, float hi)
+{
+    for (size_t i = 0; i < n; ++i)
+        vko_map(dst + i * bpv, values[i], fmt, lo, hi);
+}
+
+void vko_unmap_n(float* values, const uint8_t* src, size_t n, size_t bpv, int32_t fmt, float lo, float hi)
+{
+    for (size_t i = 0; i < n; ++i)
+        vko_unmap(values + i, src + i * bpv, fmt, lo, hi);
+}
+
 /* ---- per-voxel accessors: src/vkt/StructuredVolume.cpp:155-317 -------------------- */
 static size_t lin_index(const vko_volume* v, int32_t x, int32_t y, int32_t z)
 {

@@ -6,12 +6,11 @@
  * the timed CPU baseline in bench.py ("kind": "port").  Only tests/, __graft_entry__.smoke()
  * and bench.py's cpu_baseline leg may load it; the product library never links it.
  *
- * Parity pinning: the reference cannot be built here without writing a stand-in for its
- * CMake-generated vkt/config.h (included by src/vkt/macros.hpp:4), which this project's
- * rules forbid, and the reference ships no tests or fixtures.  This restatement is pinned
- * by the known-answer vectors that the survey recorded from the compiled reference
- * (transcribed into tests/golden/reference_kat.json), i.e. parity
- * is only partially pinned -- see DESIGN.md §3.
+ * Parity pinning: where a reference checkout is present, oracle/ref/Makefile compiles the
+ * reference's own serial sources into oracle/_ref/libvktref.so, and tests/test_reference_pin.py
+ * holds this restatement against it bit for bit (codec, Fill, Copy, arithmetic, Resample,
+ * Transform, Aggregates, Histogram); the renderers are pinned by nothing but this file -- see
+ * DESIGN.md §3.
  */
 #ifndef VKT_ORACLE_H
 #define VKT_ORACLE_H
@@ -39,6 +38,9 @@ typedef void (*vko_binary_op)(int32_t x, int32_t y, int32_t z, uint8_t* bytes1, 
 uint32_t vko_bytes_per_voxel(int32_t fmt);
 void vko_map(uint8_t* dst, float value, int32_t fmt, float lo, float hi);
 void vko_unmap(float* value, const uint8_t* src, int32_t fmt, float lo, float hi);
+/* the same over n voxels at a stride of bpv bytes; what the codec leaves alone keeps its value */
+void vko_map_n(uint8_t* dst, const float* values, size_t n, size_t bpv, int32_t fmt, float lo, float hi);
+void vko_unmap_n(float* values, const uint8_t* src, size_t n, size_t bpv, int32_t fmt, float lo, float hi);
 
 void vko_fill_range(vko_volume* v, const int32_t first[3], const int32_t last[3], float value);
 void vko_copy_range(vko_volume* dst, vko_volume* src, const int32_t first[3], const int32_t last[3],

@@ -1,6 +1,10 @@
-"""Two interchangeable executors for the same test vectors:
+"""Three interchangeable executors for the same test vectors:
 
 * ``OracleBackend`` -- the CPU restatement in oracle/ (the checker; CPU-only tests).
+* ``ReferenceBackend`` -- the reference's own serial CPU code, compiled into
+  oracle/_ref/libvktref.so where a reference checkout was present at build time (the pin
+  that the oracle and the kernels are held against in test_reference_pin.py and
+  test_gpu_reference_pin.py).
 * ``GpuBackend``    -- libvolkit through its public C ABI (volkit_amd.volkit): volumes are
   created and filled on the host under the CPU policy, the policy is switched to GPU (the
   next access migrates them to HBM), the algorithm runs as a gfx950 kernel, and the result
@@ -28,27 +32,28 @@ def codes_of(values, fmt):
 
 class OracleBackend:
     name = "oracle"
+    _b = ob  # the binding that executes; ReferenceBackend swaps it
 
     def map(self, value, fmt, lo=0.0, hi=1.0):
-        b = ob.map_voxel(value, fmt, lo, hi)
+        b = self._b.map_voxel(value, fmt, lo, hi)
         return int.from_bytes(b, "little") if b else None
 
     def fill_range(self, fmt, mapping, dims, init, first, last, value):
         v = ob.Volume(init.reshape(dims[2], dims[1], dims[0]), fmt, *mapping)
-        ob.fill_range(v, first, last, value)
+        self._b.fill_range(v, first, last, value)
         return v.codes
 
     def copy_range(self, dst_fmt, dst_map, dst_dims, dst_init, src_fmt, src_map, src_codes, first, last, off):
         d = ob.Volume(dst_init, dst_fmt, *dst_map)
         s = ob.Volume(src_codes, src_fmt, *src_map)
-        ob.copy_range(d, s, first, last, off)
+        self._b.copy_range(d, s, first, last, off)
         return d.codes
 
     def arith(self, name, fmts, maps, a, b, dst_init, first, last, off):
         d = ob.Volume(dst_init, fmts[0], *maps[0])
         s1 = ob.Volume(a, fmts[1], *maps[1])
         s2 = ob.Volume(b, fmts[2], *maps[2])
-        ob.arith_range(name, d, s1, s2, first, last, off)
+        self._b.arith_range(name, d, s1, s2, first, last, off)
         return d.codes
 
     def resample(self, dst_fmt, dst_map, dst_dims, src_fmt, src_map, src_codes, filter_mode, dst_init=None):
@@ -56,8 +61,19 @@ class OracleBackend:
         init = dst_init if dst_init is not None else np.zeros((z, y, x), dtype=CODE_DTYPE[dst_fmt])
         d = ob.Volume(init, dst_fmt, *dst_map)
         s = ob.Volume(src_codes, src_fmt, *src_map)
-        ob.resample(d, s, filter_mode)
+        self._b.resample(d, s, filter_mode)
         return d.codes
+
+
+class ReferenceBackend(OracleBackend):
+    """The same calls on oracle/_ref/libvktref.so: the reference's own compiled serial code
+    (oracle/refbinding.py).  Raises if the library has not been built."""
+    name = "reference"
+
+    def __init__(self):
+        from oracle import refbinding
+        refbinding._load()
+        self._b = refbinding
 
 
 class GpuBackend:

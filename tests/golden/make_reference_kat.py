@@ -1,12 +1,13 @@
 """Writes tests/golden/reference_kat.json: known-answer vectors observed on the COMPILED
 REFERENCE serial path during the survey, transcribed as data.
 
-Why transcription instead of regeneration: the reference's hot-path TUs include the CMake-
-generated <vkt/config.h> (reference src/vkt/macros.hpp:4) and, for Fill/Resample, the
-un-vendored visionaray headers (src/vkt/HierarchicalVolumeView.hpp:10-14).  Building them
-here would need stand-ins for generated code and a missing library, which this project does
-not write, so the reference is unbuildable in this container.  The survey ran the reference
-and recorded these outputs; they are the only reference-produced vectors available.
+These vectors were transcribed when the reference was thought unbuildable here.  Its serial
+CPU core does build (oracle/ref/Makefile: a vkt/config.h generated with every VKT_HAVE_* at 0;
+Resample.cpp and Fill.cpp alone do not, since they include HierarchicalVolumeView.hpp, which
+needs visionaray, and are driven through the reference's StructuredVolumeView instead), and
+tests/test_reference_pin.py now runs every entry of the JSON through that compiled library:
+the file stays as a record of what the survey saw, and is reproduced by the reference on
+every run where the library is built.
 
 Each entry names the SURVEY.md line that records it.  Inputs that the survey does not spell
 out (e.g. which finite values sat in a source row) are chosen so that the recorded output is
